@@ -257,6 +257,31 @@ def cpu_baseline(net, budget_s=60.0):
                                   '%d training steps after warm-up, %d threads' % (n1, threads)}}
 
 
+DUMP_BUDGET_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """Write each tensor as out_dir/<name>.npy in float32.  When all of them together exceed `budget` bytes, each one larger
+    than its share of the budget (share proportional to its size) is replaced by a fixed sample: the flat elements at
+    sorted indices drawn without replacement by numpy's default_rng(seed) -- the same positions for the same shape, so that
+    two builds compare element for element.  Returns {name: {'shape', 'sampled'}} for the result line."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(t.numel() for t in arrays.values())
+    cap = (budget - 256 * len(arrays)) // 4 - len(arrays)      # elements: room for the .npy headers and the one-element floors
+    info = {}
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        n = flat.numel()
+        keep = n if total <= cap else max(1, cap * n // total)
+        if keep < n:
+            idx = np.sort(np.random.default_rng(seed).choice(n, size=keep, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(out_dir, name + '.npy'), flat.float().cpu().numpy() if keep < n else
+                t.detach().float().cpu().numpy())
+        info[name] = {'shape': list(t.shape), 'sampled': None if keep == n else keep}
+    return info
+
+
 def _die(msg):
     print('bench.py: ' + msg, file=sys.stderr, flush=True)
     sys.exit(2)
@@ -481,9 +506,14 @@ def main():
     ap.add_argument('--dry-run', action='store_true',
                     help='validate devices / environment / rendezvous port for --gpus N and print the rank plan and gradient buckets as '
                          'one JSON line, without touching RCCL or building a model (exit code 2 if a real launch would be refused)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last timed step returned (softmax, predictions, loss) as '
+                         'DIR/<name>.npy in float32, at most 64 MB in all (a fixed, seeded sample of larger outputs); rank 0 only')
     args = ap.parse_args()
     if args.gpus < 1:
         _die('--gpus must be >= 1')
+    if args.steps < 1:
+        _die('--steps must be >= 1')
     if args.dry_run:
         dry_run_plan(args)                   # does not return
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
@@ -536,8 +566,9 @@ def main():
 
     def one_step(i):
         img, seg, keep = batches[i % len(batches)]
-        trainer.train_step(img, seg, want_outputs=True)    # (softmax, predictions, loss) as train2D.py:87-103 returns
+        out = trainer.train_step(img, seg, want_outputs=True)    # (softmax, predictions, loss) as train2D.py:87-103 returns
         trainer.model.reset_states_per_batch(keep)
+        return out
 
     for i in range(args.warmup):
         one_step(i)
@@ -547,10 +578,14 @@ def main():
     ms0 = torch.cuda.memory_stats(dev)
     t0 = time.perf_counter()
     for i in range(args.steps):
-        one_step(args.warmup + i)
+        last = one_step(args.warmup + i)
     torch.cuda.synchronize()
     dp.barrier()
     elapsed = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
+    # the last timed step's results, copied out before any later step can reuse their buffers
+    dumped = dump_outputs(args.dump_outputs, dict(zip(('softmax', 'predictions', 'loss'), last))) \
+        if (args.dump_outputs and dp.rank == 0) else None
+    del last
     if dp.collectives:
         torch.distributed.all_reduce(elapsed, op=torch.distributed.ReduceOp.MAX)
     elapsed = float(elapsed.item())
@@ -840,6 +875,8 @@ def main():
             'variants': variants,
             'roofline': roofline, 'cpu_baseline': cpu,
         }
+        if dumped is not None:
+            line['dumped_outputs'] = dumped
         sys.stdout.flush()
         os.dup2(real_stdout, 1)
         print(json.dumps(line), flush=True)

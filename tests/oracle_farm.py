@@ -124,9 +124,11 @@ class Farm(object):
         sp, out = os.path.join(self.dir, key + '.json'), os.path.join(self.dir, key + '.npz')
         with open(sp, 'w') as f:
             json.dump(spec, f)
+        import gpu_slots
+        gpu_slots.slot_dir()                 # the session's slot directory, inherited by the worker
         env = dict(os.environ)
         env['OMP_NUM_THREADS'] = str(int(spec.get('threads', 16)))
-        env['HIP_VISIBLE_DEVICES'] = ''      # a worker never touches the GPU
+        env['HIP_VISIBLE_DEVICES'] = ''      # a worker computes on the host only
         log = open(os.path.join(self.dir, key + '.log'), 'w')
         p = subprocess.Popen([sys.executable, os.path.abspath(__file__), sp, self.params_path, out], stdout=log, stderr=log, env=env)
         self.jobs[key] = (p, out, log, time.time())
@@ -165,6 +167,11 @@ if __name__ == '__main__':
         spec_ = json.load(f)
     with np.load(params_path) as z:
         params_ = {k: z[k] for k in z.files}
+    if spec_.get('kind') != 'forward':
+        # the first autograd backward opens the GPU (torch's engine asks the HIP backend for its device count), host-only or not:
+        # a gradient job takes one of the session's GPU process slots and keeps it until it exits (forward jobs run under no_grad)
+        import gpu_slots
+        _slot = gpu_slots.acquire(1)
     res = run_job(spec_, params_)
     tmp = out_path + '.tmp.npz'
     np.savez(tmp, **res)

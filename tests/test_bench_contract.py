@@ -88,7 +88,12 @@ def _finish_bench(p, timeout=900):
 
 
 def _run_bench(extra, env_extra, timeout=900):
-    return _finish_bench(_start_bench(extra, env_extra), timeout)
+    import gpu_slots
+    gpus = int(extra[extra.index('--gpus') + 1]) if '--gpus' in extra else 1
+    launches = gpus > 1 and '--dry-run' not in extra and 'WORLD_SIZE' not in env_extra
+    # bench.py itself, and when it self-launches: the torch.distributed.run agent and one process per rank
+    with gpu_slots.hold(gpus + 2 if launches else 1):
+        return _finish_bench(_start_bench(extra, env_extra), timeout)
 
 
 def test_bench_refuses_mismatched_launches():
@@ -108,12 +113,24 @@ SMALL = ['--steps', '2', '--warmup', '1', '--size', '64', '--batch', '1', '--unr
 def test_bench_self_launches_n_ranks(backend):
     """`python bench.py --gpus 2` (no launcher) must start two ranks by itself and say what the collective layer saw.
     gloo: both ranks share the one GPU of the test box (control flow of the whole DP bench path on the HIP kernels);
-    nccl (= RCCL): one device per rank, skipped on a box with fewer than two."""
+    nccl (= RCCL): one device per rank; a box with fewer than two must refuse `--gpus 2`, and runs the RCCL path of the bench as
+    a forced world of one instead (--force-collectives: process group, gradient buckets, loss sums and SyncBN statistics through
+    real RCCL all-reduce calls on the one GPU)."""
     import torch
     if backend == 'nccl' and torch.cuda.device_count() < 2:
         rc, line, err = _run_bench(['--gpus', '2'] + SMALL, {'LU_DP_BACKEND': 'nccl'})
         assert rc == 2 and line is None and 'needs 2 visible GPUs' in err      # refuses instead of measuring one GPU
-        pytest.skip('RCCL needs one device per rank: %d visible' % torch.cuda.device_count())
+        rc, line, err = _run_bench(['--gpus', '1', '--sync-bn', '--force-collectives'] + SMALL, {'LU_DP_BACKEND': 'nccl'})
+        assert rc == 0 and line is not None, err
+        dp = line['dp']
+        assert dp['backend'] == 'nccl' and dp['world_size'] == 1 and dp['forced_world_of_one'] and line['n_gpus'] == 1
+        tr = dp['bucket_trace']
+        assert tr and all(b['bytes'] > 0 for b in tr) and sum(b['bytes'] for b in tr) == sum(dp['gradient_bucket_bytes'])
+        assert tr[0]['issued_ms_before_backward_end'] > 0 and dp['exposed_allreduce_ms'] is not None
+        assert dp['allreduce_launches_per_step'] >= 1 and dp['allreduce_ms_per_step'] > 0 and dp['syncbn_allreduces_per_step'] == 32
+        assert abs(line['value'] - 1 * 1 * 2 / (line['ms_per_step'] * 1e-3)) <= 0.01 * line['value']
+        print('bench --gpus 1 --force-collectives over nccl: %s' % {k: dp[k] for k in dp if k != 'devices'})
+        return
     rc, line, err = _run_bench(['--gpus', '2', '--sync-bn', '--check'] + SMALL, {'LU_DP_BACKEND': backend})
     assert rc == 0 and line is not None, err
     # --check: the DP == single-process comparison ran inline before the timing, and the overlap proof is on the line
@@ -167,3 +184,44 @@ def test_bench_dry_run_on_the_gpu_box():
         assert rc == 2 and any('one device per rank' in p for p in line['problems'])
     else:
         assert rc == 0 and line['ok']
+
+
+def test_dump_outputs_sampling_is_fixed_and_within_budget(tmp_path):
+    """`--dump-outputs`: float32 files, at most the byte budget in all, and a larger output replaced by the same sample every time."""
+    import numpy as np
+    import torch
+    b = _bench()
+    big = torch.arange(3 * 1000, dtype=torch.float32).view(10, 100, 3)
+    arrays = {'softmax': big, 'loss': torch.tensor([0.5])}
+    info = b.dump_outputs(str(tmp_path / 'a'), arrays, budget=4 * 1000)
+    b.dump_outputs(str(tmp_path / 'b'), arrays, budget=4 * 1000)
+    sizes = 0
+    for name in arrays:
+        a_, b_ = np.load(tmp_path / 'a' / (name + '.npy')), np.load(tmp_path / 'b' / (name + '.npy'))
+        assert a_.dtype == np.float32 and np.array_equal(a_, b_)
+        sizes += os.path.getsize(tmp_path / 'a' / (name + '.npy'))      # what lands on disk, headers included
+    assert sizes <= 4 * 1000 and info['softmax']['sampled'] and info['loss']['sampled'] is None
+    s = np.load(tmp_path / 'a' / 'softmax.npy')
+    assert np.all(np.diff(s) > 0) and set(s.tolist()) <= set(big.view(-1).tolist())      # sorted positions of the real elements
+    # under the budget: the arrays themselves, full shape
+    b.dump_outputs(str(tmp_path / 'c'), arrays)
+    assert np.array_equal(np.load(tmp_path / 'c' / 'softmax.npy'), big.numpy())
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_repeat_identically(tmp_path):
+    """Two runs with the same arguments time exactly --steps steps and dump identical outputs of the last timed step."""
+    import numpy as np
+    args = ['--steps', '3', '--warmup', '1', '--size', '64', '--batch', '2', '--unroll', '2', '--no-cpu-baseline', '--no-infer',
+            '--no-bf16', '--no-x3', '--no-variants']
+    dumps = []
+    for run in ('a', 'b'):
+        rc, line, err = _run_bench(args + ['--dump-outputs', str(tmp_path / run)], {})
+        assert rc == 0 and line is not None, err
+        assert line['steps'] == 3 and line['ms_per_step'] > 0 and 'ms_per_step' in line
+        assert set(line['dumped_outputs']) == {'softmax', 'predictions', 'loss'}
+        dumps.append({n: np.load(tmp_path / run / (n + '.npy')) for n in line['dumped_outputs']})
+    for n, a_ in dumps[0].items():
+        assert a_.dtype == np.float32 and np.isfinite(a_).all() and np.array_equal(a_, dumps[1][n]), n
+    assert sorted(dumps[0]['softmax'].shape) == [2, 2, 3, 64, 64] and dumps[0]['loss'].shape == (1,)
+    assert sum(os.path.getsize(tmp_path / 'a' / (n + '.npy')) for n in dumps[0]) <= 64 * 2 ** 20

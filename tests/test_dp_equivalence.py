@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import gpu_slots
 from conftest import tiny_net
 from engine_backend import engine_backend
 
@@ -53,11 +54,12 @@ def test_dp2_equals_single_process(tmp_path):
     script.write_text(WORKER % {'root': ROOT, 'tmp': str(tmp_path)})
     for sync_bn in (1, 0):
         port = 29600 + (os.getpid() + sync_bn) % 1500
-        procs = [subprocess.Popen([sys.executable, str(script), str(sync_bn)],
-                                  env=dict(os.environ, RANK=str(r), WORLD_SIZE='2', LOCAL_RANK=str(r),
-                                           MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port)),
-                                  stdout=subprocess.PIPE, stderr=subprocess.STDOUT) for r in range(2)]
-        outs = [p.communicate(timeout=900)[0].decode() for p in procs]
+        with gpu_slots.hold(2):
+            procs = [subprocess.Popen([sys.executable, str(script), str(sync_bn)],
+                                      env=dict(os.environ, RANK=str(r), WORLD_SIZE='2', LOCAL_RANK=str(r),
+                                               MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port)),
+                                      stdout=subprocess.PIPE, stderr=subprocess.STDOUT) for r in range(2)]
+            outs = [p.communicate(timeout=900)[0].decode() for p in procs]
         for p, o in zip(procs, outs):
             assert p.returncode == 0, o[-3000:]
     with engine_backend('emu'):
@@ -144,9 +146,10 @@ def test_dp2_syncbn_on_the_hip_kernels_equals_single_process(tmp_path, precision
     limits apply -- gradients to summation-order noise."""
     import train2D
     import Networks
-    h = _launch_dp2(tmp_path, precision)
-    tmp_path, procs, x, gt = h['tmp'], h['procs'], h['x'], h['gt']
-    outs = [p.communicate(timeout=900)[0].decode() for p in procs]
+    with gpu_slots.hold(2):
+        h = _launch_dp2(tmp_path, precision)
+        tmp_path, procs, x, gt = h['tmp'], h['procs'], h['x'], h['gt']
+        outs = [p.communicate(timeout=900)[0].decode() for p in procs]
     for p, o in zip(procs, outs):
         assert p.returncode == 0, o[-3000:]
     net = tiny_net(3, (64, 16, 16, 64), (16, 8, 8, 8)) if precision == 'bf16x3' else tiny_net(3, (32, 16, 16, 32), (16, 8, 8, 8))
@@ -176,8 +179,12 @@ def test_dp2_syncbn_on_the_hip_kernels_equals_single_process(tmp_path, precision
     assert diff.max() <= 2.5e-3 and (diff > 1e-4).mean() <= frac, (diff.max(), (diff > 1e-4).mean())
 
 
-def _launch_dp8_syncbn(tmp_path):
-    W = 8
+# ranks that share the one GPU of the test box: with the pytest process itself, at most six processes hold the GPU at once
+ONE_GPU_RANKS = 5
+
+
+def _launch_dp5_syncbn(tmp_path):
+    W = ONE_GPU_RANKS
     rng = np.random.default_rng(8)
     x = rng.standard_normal((W, 3, 1, 24, 32)).astype(np.float32)
     gt = rng.integers(-1, 3, size=(W, 3, 1, 24, 32)).astype(np.float32)
@@ -193,17 +200,19 @@ def _launch_dp8_syncbn(tmp_path):
 
 
 @pytest.mark.gpu
-def test_dp8_syncbn_three_buckets_over_gloo_on_one_gpu_equals_single_process(tmp_path):
-    """EIGHT ranks x 1 slot on the real kernels (gloo, all on the one GPU of the test box): shard_slots
-    with W = 8, SyncBN with 8 contributors, the gradient all-reduce in THREE OR MORE buckets (a small bucket size: the tiny
-    net's 0.1 MB of gradients would otherwise leave as one), loss sums over 8 ranks -- loss and pre-Adam gradients must equal
-    the single-process step on the 8-slot batch.  What an 8-GPU box adds to this is RCCL itself and one device per rank."""
+def test_dp5_syncbn_three_buckets_over_gloo_on_one_gpu_equals_single_process(tmp_path):
+    """FIVE ranks x 1 slot on the real kernels (gloo, all on the one GPU of the test box): shard_slots
+    with W = 5 (not a power of two), SyncBN with 5 contributors, the gradient all-reduce in THREE OR MORE buckets (a small bucket
+    size: the tiny net's 0.1 MB of gradients would otherwise leave as one), loss sums over 5 ranks -- loss and pre-Adam
+    gradients must equal the single-process step on the 5-slot batch.  Five, not eight: with the pytest process, six processes
+    hold the one GPU, the most a shared box allows.  What a multi-GPU box adds to this is RCCL itself and one device per rank."""
     import train2D
     import Networks
-    W = 8
-    h = _launch_dp8_syncbn(tmp_path)
-    tmp_path, procs, x, gt = h['tmp'], h['procs'], h['x'], h['gt']
-    outs = [p.communicate(timeout=900)[0].decode() for p in procs]
+    W = ONE_GPU_RANKS
+    with gpu_slots.hold(W):
+        h = _launch_dp5_syncbn(tmp_path)
+        tmp_path, procs, x, gt = h['tmp'], h['procs'], h['x'], h['gt']
+        outs = [p.communicate(timeout=900)[0].decode() for p in procs]
     for p, o in zip(procs, outs):
         assert p.returncode == 0, o[-3000:]
     net = tiny_net(3, (32, 16, 16, 32), (16, 8, 8, 8))
@@ -215,8 +224,8 @@ def test_dp8_syncbn_three_buckets_over_gloo_on_one_gpu_equals_single_process(tmp
     got = np.load(tmp_path / 'dp_gpu_out.npz')
     g_err = np.abs(got['grads1'] - ref_grads1).max() / np.abs(ref_grads1).max()
     ranges = got['ranges']
-    print('dp8 over gloo on one GPU vs single: loss err %.3e, step-1 gradient err / max|g| %.3e, %d buckets %s' %
-          (np.abs(got['loss'] - np.array([float(l1), float(l2)])).max(), g_err, len(ranges), ranges.tolist()))
+    print('dp%d over gloo on one GPU vs single: loss err %.3e, step-1 gradient err / max|g| %.3e, %d buckets %s' %
+          (W, np.abs(got['loss'] - np.array([float(l1), float(l2)])).max(), g_err, len(ranges), ranges.tolist()))
     assert np.abs(got['loss'] - np.array([float(l1), float(l2)])).max() <= 1e-5 and g_err <= 2e-6
     # buckets: at least three, contiguous, covering the flat gradient buffer front to back (backward-completion order)
     assert len(ranges) >= 3 and ranges[0][0] == 0 and ranges[-1][1] == tr.engine.n_flat
@@ -232,7 +241,8 @@ import numpy as np, torch
 from conftest import tiny_net
 import train2D, Networks
 from lu_native.dp import DataParallel
-dp = DataParallel(backend='nccl')       # RCCL: one device per rank (LOCAL_RANK)
+dp = DataParallel(backend='nccl', force=True)       # RCCL: one device per rank (LOCAL_RANK); a world of one still all-reduces
+assert dp.collectives and dp.world_size == int(os.environ['WORLD_SIZE'])
 assert torch.distributed.get_backend() == 'nccl' and torch.cuda.current_device() == dp.local_rank
 d = np.load(os.path.join(%(tmp)r, 'batch.npz'))
 net = tiny_net(3, (32, 16, 16, 32), (16, 8, 8, 8))
@@ -254,13 +264,13 @@ torch.distributed.destroy_process_group()
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('n_ranks', [2, 4, 8])
-def test_dpN_syncbn_over_rccl_equals_single_process(tmp_path, n_ranks):
-    """The self-check for the first multi-GPU box: N ranks, one device each, backend nccl (= RCCL over xGMI), SyncBN:
-    loss and pre-Adam gradients must equal the single-process step on the N-slot batch (fp32: summation-order noise).
-    Skipped when the box has fewer than N devices (the one-GPU test box runs the gloo variant above instead)."""
-    if torch.cuda.device_count() < n_ranks:
-        pytest.skip('needs %d GPUs, %d visible' % (n_ranks, torch.cuda.device_count()))
+def test_dp_syncbn_over_rccl_one_rank_per_device_equals_single_process(tmp_path):
+    """The self-check for a multi-GPU box: N ranks, one device each, backend nccl (= RCCL over xGMI), SyncBN: loss and pre-Adam
+    gradients must equal the single-process step on the N-slot batch (fp32: summation-order noise).  N = every visible device, at
+    most ONE_GPU_RANKS (with pytest, six processes hold GPUs).  RCCL refuses two ranks on one device, so a one-GPU box runs N = 1
+    with the collectives forced on: the process group, the gradient buckets, the loss sums and the SyncBN statistics still go
+    through real RCCL all-reduce calls (the N-rank control flow on one GPU: the gloo tests above)."""
+    n_ranks = max(1, min(torch.cuda.device_count(), ONE_GPU_RANKS))
     import train2D
     import Networks
     rng = np.random.default_rng(n_ranks)
@@ -271,11 +281,12 @@ def test_dpN_syncbn_over_rccl_equals_single_process(tmp_path, n_ranks):
     script.write_text(RCCL_WORKER % {'root': ROOT, 'tmp': str(tmp_path)})
     port = 29600 + (os.getpid() + 7 * n_ranks) % 1500
     env = {k: v for k, v in os.environ.items() if k != 'LU_DP_BACKEND'}
-    procs = [subprocess.Popen([sys.executable, str(script), 'fp32'],
-                              env=dict(env, RANK=str(r), WORLD_SIZE=str(n_ranks), LOCAL_RANK=str(r), MASTER_ADDR='127.0.0.1',
-                                       MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY='0'),
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT) for r in range(n_ranks)]
-    outs = [p.communicate(timeout=900)[0].decode() for p in procs]
+    with gpu_slots.hold(n_ranks):
+        procs = [subprocess.Popen([sys.executable, str(script), 'fp32'],
+                                  env=dict(env, RANK=str(r), WORLD_SIZE=str(n_ranks), LOCAL_RANK=str(r), MASTER_ADDR='127.0.0.1',
+                                           MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY='0'),
+                                  stdout=subprocess.PIPE, stderr=subprocess.STDOUT) for r in range(n_ranks)]
+        outs = [p.communicate(timeout=900)[0].decode() for p in procs]
     for p, o in zip(procs, outs):
         assert p.returncode == 0, o[-3000:]
     net = tiny_net(3, (32, 16, 16, 32), (16, 8, 8, 8))
@@ -289,6 +300,7 @@ def test_dpN_syncbn_over_rccl_equals_single_process(tmp_path, n_ranks):
     print('dp%d over RCCL vs single: loss err %.3e, step-1 gradient err / max|g| %.3e, all-reduce launches %d' %
           (n_ranks, np.abs(got['loss'] - np.array([float(l1), float(l2)])).max(), g_err, int(got['launched'][0])))
     assert np.abs(got['loss'] - np.array([float(l1), float(l2)])).max() <= 1e-5 and g_err <= 2e-6
+    assert int(got['launched'][0]) >= 2                     # gradient buckets of both steps went through RCCL
 
 
 FORCED_WORKER = r"""
@@ -346,9 +358,10 @@ def test_dp1_rccl_forced_collectives_equals_plain_step(tmp_path, precision):
     port = 29600 + (os.getpid() + 13) % 1500
     env = {k: v for k, v in os.environ.items() if k not in ('LU_DP_BACKEND', 'LU_DP_FORCE', 'RANK', 'WORLD_SIZE', 'LOCAL_RANK')}
     for mode in ('forced', 'plain'):
-        p = subprocess.run([sys.executable, str(script), precision, mode],
-                           env=dict(env, MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY='0'),
-                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
+        with gpu_slots.hold(1):
+            p = subprocess.run([sys.executable, str(script), precision, mode],
+                               env=dict(env, MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY='0'),
+                               stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
         assert p.returncode == 0, p.stdout.decode()[-3000:]
     a, b = np.load(tmp_path / 'dp1_forced.npz'), np.load(tmp_path / 'dp1_plain.npz')
     ranges = a['ranges']
@@ -402,8 +415,9 @@ def test_dp1_forced_collectives_over_gloo_equals_plain_step(tmp_path):
     script = tmp_path / 'worker_forced_gloo.py'
     script.write_text(FORCED_GLOO_WORKER % {'root': ROOT, 'tmp': str(tmp_path)})
     env = {k: v for k, v in os.environ.items() if k not in ('LU_DP_BACKEND', 'LU_DP_FORCE', 'RANK', 'WORLD_SIZE', 'LOCAL_RANK')}
-    p = subprocess.run([sys.executable, str(script)], env=dict(env, MASTER_ADDR='127.0.0.1', MASTER_PORT=str(29600 + (os.getpid() + 29) % 1500)),
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
+    with gpu_slots.hold(1):
+        p = subprocess.run([sys.executable, str(script)], env=dict(env, MASTER_ADDR='127.0.0.1', MASTER_PORT=str(29600 + (os.getpid() + 29) % 1500)),
+                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
     assert p.returncode == 0, p.stdout.decode()[-3000:]
     d = np.load(tmp_path / 'dp1_gloo.npz')
     r = d['forced_ranges']

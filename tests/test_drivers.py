@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import gpu_slots
 from conftest import tiny_net
 from engine_backend import engine_backend
 
@@ -175,6 +176,10 @@ with engine_backend(os.environ.get('LU_TEST_BACKEND', 'emu')):
     tail = collectives[-n_bn:]
     print('RANK', rank, 'steps', trainer.step, 'tail', len(tail), flush=True)
     np.save(os.path.join(%(tmp)r, 'done_%%d.npy' %% rank), np.array([trainer.step, len(collectives)]))
+# tear the gloo process group down before interpreter exit, as the other multi-rank workers do (test_dp_equivalence.py): left
+# to the shutdown, its native threads can outlive it and abort the process ("terminate called without an active exception")
+torch.distributed.barrier()
+torch.distributed.destroy_process_group()
 '''
 
 
@@ -190,11 +195,12 @@ def test_dp_loop_failure_on_one_rank_stops_all_ranks_without_hanging(tmp_path, e
     script = tmp_path / 'worker.py'
     script.write_text(DP_LOOP_WORKER % {'root': root, 'tmp': str(tmp_path)})
     port = 29700 + os.getpid() % 1200 + (0 if err_kind == 'ValueError' else 1201)
-    procs = [subprocess.Popen([sys.executable, str(script)],
-                              env=dict(os.environ, RANK=str(r), WORLD_SIZE='2', LOCAL_RANK=str(r), LU_DP_BACKEND='gloo',
-                                       LU_TEST_ERR=err_kind, MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port)),
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT) for r in range(2)]
-    outs = [p.communicate(timeout=600)[0].decode() for p in procs]
+    with gpu_slots.hold(2):
+        procs = [subprocess.Popen([sys.executable, str(script)],
+                                  env=dict(os.environ, RANK=str(r), WORLD_SIZE='2', LOCAL_RANK=str(r), LU_DP_BACKEND='gloo',
+                                           LU_TEST_ERR=err_kind, MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port)),
+                                  stdout=subprocess.PIPE, stderr=subprocess.STDOUT) for r in range(2)]
+        outs = [p.communicate(timeout=600)[0].decode() for p in procs]
     for p, o in zip(procs, outs):
         assert p.returncode == 0, o[-3000:]
     a, b = np.load(tmp_path / 'done_0.npy'), np.load(tmp_path / 'done_1.npy')
@@ -213,14 +219,18 @@ def test_dp_loop_failure_on_one_rank_stops_all_ranks_without_hanging(tmp_path, e
     assert os.path.exists(os.path.join(run_dir, 'model.ckpt.index'))
 
 
-def _launch_dp8_loop(tmp_path):
+# ranks that share the one GPU of the test box: with the pytest process itself, at most six processes hold the GPU at once
+ONE_GPU_RANKS = 5
+
+
+def _launch_dp5_loop(tmp_path):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     script = tmp_path / 'worker.py'
     script.write_text(DP_LOOP_WORKER % {'root': root, 'tmp': str(tmp_path)})
     port = 29700 + (os.getpid() + 77) % 1200
-    W = 8
+    W = ONE_GPU_RANKS
     procs = [subprocess.Popen([sys.executable, str(script)],
                               env=dict(os.environ, RANK=str(r), WORLD_SIZE=str(W), LOCAL_RANK='0', LU_DP_BACKEND='gloo',
                                        LU_TEST_BACKEND='hip', LU_TEST_ERR='ValueError', MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port)),
@@ -229,15 +239,17 @@ def _launch_dp8_loop(tmp_path):
 
 
 @pytest.mark.gpu
-def test_dp8_loop_on_one_gpu_failure_agreement_and_per_rank_state_files(tmp_path):
-    """EIGHT ranks over gloo on the one GPU of the test box, HIP kernels underneath (make the first
-    8-GPU box boring): the training loop of train2D with 8 contributors -- slot sharding, the per-step failure flag, a reader
+def test_dp5_loop_on_one_gpu_failure_agreement_and_per_rank_state_files(tmp_path):
+    """FIVE ranks over gloo on the one GPU of the test box, HIP kernels underneath (make the first
+    multi-GPU box boring): the training loop of train2D with 5 contributors -- slot sharding, the per-step failure flag, a reader
     error on the LAST rank at iteration 5 that every rank must leave the loop with at the same step, the collective error-path
-    checkpoint (BatchNorm statistics averaged over 8 ranks), one run directory, eight rotating per-rank state files."""
-    W = 8
-    h = _launch_dp8_loop(tmp_path)
-    tmp_path, procs = h['tmp'], h['procs']
-    outs = [p.communicate(timeout=900)[0].decode() for p in procs]
+    checkpoint (BatchNorm statistics averaged over 5 ranks), one run directory, five rotating per-rank state files.  Five, not
+    eight: with the pytest process, six processes hold the one GPU, the most a shared box allows."""
+    W = ONE_GPU_RANKS
+    with gpu_slots.hold(W):
+        h = _launch_dp5_loop(tmp_path)
+        tmp_path, procs = h['tmp'], h['procs']
+        outs = [p.communicate(timeout=900)[0].decode() for p in procs]
     for p, o in zip(procs, outs):
         assert p.returncode == 0, o[-3000:]
     done = [np.load(tmp_path / ('done_%d.npy' % r)) for r in range(W)]

@@ -249,13 +249,15 @@ def test_dp_bucketed_allreduce_world2_gloo(tmp_path):
     script = tmp_path / 'dp_worker.py'
     script.write_text(DP_WORKER % {'root': ROOT})
     port = 29500 + os.getpid() % 2000
+    import gpu_slots
     procs = []
-    for rank in range(2):
-        env = dict(os.environ, RANK=str(rank), WORLD_SIZE='2', LOCAL_RANK=str(rank), MASTER_ADDR='127.0.0.1',
-                   MASTER_PORT=str(port))
-        procs.append(subprocess.Popen([sys.executable, str(script)], env=env, stdout=subprocess.PIPE,
-                                      stderr=subprocess.STDOUT))
-    outs = [p.communicate(timeout=120)[0].decode() for p in procs]
+    with gpu_slots.hold(2):
+        for rank in range(2):
+            env = dict(os.environ, RANK=str(rank), WORLD_SIZE='2', LOCAL_RANK=str(rank), MASTER_ADDR='127.0.0.1',
+                       MASTER_PORT=str(port))
+            procs.append(subprocess.Popen([sys.executable, str(script)], env=env, stdout=subprocess.PIPE,
+                                          stderr=subprocess.STDOUT))
+        outs = [p.communicate(timeout=120)[0].decode() for p in procs]
     for p, o in zip(procs, outs):
         assert p.returncode == 0, o
         assert 'ok' in o
@@ -277,3 +279,30 @@ def test_tensorboard_event_writer(tmp_path):
     import io
     img = np.asarray(Image.open(io.BytesIO(ev[2][1]['Image'][3])))
     assert img.shape == (6, 7) and img[0, 0] == 0 and img[-1, -1] == 255
+
+
+def test_gpu_slots_bound_the_processes_a_session_starts(tmp_path, monkeypatch):
+    """tests/gpu_slots.py: while the session's slots are all held, another process waits for one; a holder that dies (even
+    killed) gives its slot back."""
+    import time
+    import gpu_slots
+    monkeypatch.setenv('LU_GPU_SLOT_DIR', str(tmp_path))
+    child = ("import sys, time; sys.path.insert(0, %r); import gpu_slots; gpu_slots.acquire(1); print(time.time(), flush=True)"
+             % os.path.join(ROOT, 'tests'))
+    with gpu_slots.hold(gpu_slots.SLOTS):
+        p = subprocess.Popen([sys.executable, '-c', child], stdout=subprocess.PIPE)
+        time.sleep(2.0)
+        assert p.poll() is None                      # still waiting: every slot is taken
+        released = time.time()
+    assert float(p.communicate(timeout=60)[0]) >= released
+    holder = subprocess.Popen([sys.executable, '-c', child.replace('flush=True)', 'flush=True); time.sleep(600)')],
+                              stdout=subprocess.PIPE)
+    holder.stdout.readline()                         # it holds one slot now
+    t0 = time.time()
+    held = gpu_slots.acquire(gpu_slots.SLOTS - 1)    # the rest are free ...
+    holder.kill()
+    holder.wait()
+    held += gpu_slots.acquire(1)                     # ... and the killed holder's slot comes back
+    assert time.time() - t0 < 30 and len(held) == gpu_slots.SLOTS
+    for f in held:
+        f.close()
