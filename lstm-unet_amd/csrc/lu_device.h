@@ -8,9 +8,21 @@
 #include "../../include/lstm_unet_hip.h"
 
 #ifdef LU_EMU
+#include <string>
 #include "emu_runtime.h"
+// launch record of the emulator build (tests/test_dispatch_coverage.py): the kernel instance of every launch as spelled at its launch
+// site, '\n'-separated, kept while switched on (tests/emu/emu_launches.cpp exports the switch and the reader)
+namespace lu_launch_record {
+inline bool on = false;
+inline std::string text;
+inline void add(const char* kernel) {
+    if (!on) return;
+    text += kernel;
+    text += '\n';
+}
+}  // namespace lu_launch_record
 #define LU_LAUNCH(kernel, grid, block, stream, ...) \
-    lu_emu::launch((grid), (block), [=]() { kernel(__VA_ARGS__); })
+    (lu_launch_record::add(#kernel), lu_emu::launch((grid), (block), [=]() { kernel(__VA_ARGS__); }))
 #define LU_LAUNCH_DYN(kernel, grid, block, lds_bytes, stream, ...) LU_LAUNCH(kernel, grid, block, stream, __VA_ARGS__)
 #define LU_DYN_LDS(type, name) type* name = reinterpret_cast<type*>(lu_emu::g_dyn_lds)
 static inline f32x16 lu_mfma(float a, float b, f32x16 c) { return lu_emu::mfma_32x32x2(a, b, c); }

@@ -912,7 +912,7 @@ __global__ void window_copy_kernel(const float* __restrict__ x, int x_ps, float*
             ok = sy >= 0 && sy < Hx && sx >= 0 && sx < Wx;
         }
         const float v = ok ? x[((f * Hx + sy) * Wx + sx) * x_ps + c] : 0.f;
-        y[i] = (beta != 0.f ? beta * y[i] : 0.f) + v;
+        y[i] = beta != 0.f ? beta * y[i] + v : v;      // beta == 0: a pure copy (callers move bf16 pairs as floats: -0, sNaN bits)
     }
 }
 

@@ -860,9 +860,9 @@ class Engine:
             return t6
         if out is None:
             out = torch.empty((fr, H, Wp, C6), device=t6.device, dtype=t6.dtype)
-        if C6 % 8 == 0 and t6.is_contiguous() and out.is_contiguous():
+        if C6 % 8 == 0 and t6.is_contiguous() and out.is_contiguous() and t6.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0:
             # the library's window copy (zero fill outside) on the rows seen as fp32: 16-byte transactions, one launch -- as a torch
-            # strided copy of 2-byte elements this was 74 ms of a config-4 step
+            # strided copy of 2-byte elements this was 74 ms of a config-4 step (16-byte aligned: the 16-byte form, a pure bit mover)
             ops.window_copy(t6.view(torch.float32), (H, Wp), (0, 0), 0, out=out.view(torch.float32))
         else:
             out[:, :, W:].zero_()

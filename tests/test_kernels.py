@@ -830,6 +830,27 @@ def test_window_copy_reflect_crop_embed(be):
     assert np.array_equal(be.host(wide), exp8)
 
 
+def test_window_copy_moves_bits_on_unaligned_pointers(be):
+    """beta == 0 is a pure copy on BOTH paths: engine._x3_pad_w moves bf16 split6 rows through lu_window_copy viewed as fp32, so a
+    bf16 pair that forms fp32 -0.0, denormal halves and a signalling NaN must come out bit-identical -- pointers one float off 16-byte
+    alignment take the scalar kernel, aligned ones the 16-byte kernel; the zero fill outside the window is +0.0."""
+    halves = np.array([0x0000, 0x8000, 0x0001, 0x8001, 0x007f, 0x807f, 0x0001, 0x7f80, 0x0001, 0xff80, 0x3f80, 0xbf80,
+                       0x0000, 0x0080, 0x0040, 0x7fa0], np.uint16)
+    fr, H, W, Wp, C = 2, 3, 5, 8, 8                                     # 16 bf16 = 8 floats per pixel; rows padded 5 -> 8 pixels
+    pix = np.random.default_rng(5).permutation(np.tile(halves, fr * H * W)).reshape(fr, H, W, 2 * C)
+    pix[0, 0, 0] = halves                                               # the pairs in order: -0.0, denormals, sNaN, -sNaN, 1, -1, ...
+    bits = pix.view(np.uint32)                                          # [fr, H, W, C] fp32 bit patterns
+    for off in (1, 0):                                                  # scalar path, then the 16-byte one
+        lead = 4 - off                                                  # (the buffers themselves are 16-byte aligned)
+        xd = be.dev(np.concatenate([np.zeros(lead, np.uint32), bits.reshape(-1)]).view(np.int32), np.int32)
+        yd = be.dev(np.full(fr * H * Wp * C + lead, 0x7fa5a5a5, np.uint32).view(np.int32), np.int32)
+        ck(be, be.lib.lu_window_copy(be.ptr(xd, lead), C, be.ptr(yd, lead), fr, H, W, H, Wp, C, 0, 0, 0, 0.0, be.stream),
+           'window copy bits')
+        y = be.host(yd).view(np.uint32)[lead:].reshape(fr, H, Wp, C)
+        assert np.array_equal(y[:, :, :W], bits), 'offset %d: bit patterns changed' % off
+        assert not y[:, :, W:].any(), 'offset %d: the zero fill is not +0.0' % off
+
+
 def test_softmax_wce(be):
     rows = 1000
     lg = rnd(rows, 3, scale=2.0)
